@@ -1,6 +1,6 @@
 """Benchmark of the asyncmap! hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c1..c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c1..c5] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 (`bench.py --gpus N` alone starts the N ranks itself, under torch.distributed.run as a child
 process, and relays rank 0's line.)
@@ -16,8 +16,12 @@ shared-memory mailboxes.  Inputs are generated on the de
 iterations/sec of the whole job (K / max over ranks of the timed region).
 
 Rank 0 prints one JSON line with the roofline of the dominant kernel (lsq_grad_kernel, HIP
-events on the stream it runs on, all ranks) and, at N = 1, the CPU baseline
+events on the stream it runs on, all ranks).  A plain run does no more than that line needs:
+set up, warm up, time the K steps.  `--full` adds, at N = 1, what takes runs of its own: the
+same loop driven from Python (c1, c2), the measured HBM read ceiling and the CPU baseline
 (oracle/cpu_baseline: the C restatement of the reference's coordinator + worker threads).
+`--dump-outputs DIR` writes the iterate, the gathered gradients and their epochs as they
+stand after the last timed step (DIR/x.npy, recvbuf.npy, repochs.npy).
 """
 import argparse
 import json
@@ -90,8 +94,15 @@ def parse():
     p.add_argument("--warmup", type=int, default=30)
     p.add_argument("--config", default="c2", choices=sorted(CONFIGS))
     p.add_argument("--seed", type=int, default=1234)
-    p.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline sample length")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="beside the headline figure, everything else the benchmark measures at N = 1: the "
+                        "same loop driven from Python (c1, c2), the measured HBM read ceiling and the CPU "
+                        "baseline (c1, c2); a plain run sets up, warms up, times the steps and prints its line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the coordinator loop left its caller after the last "
+                        "one (x, recvbuf, repochs) as DIR/<name>.npy (float32, float64 for an fp64 config)")
+    p.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline sample length (--full)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without its CPU baseline")
     p.add_argument("--timing-period", type=int, default=None,
                    help="time one in every k launches with HIP events (default: the config's, 1 or 16 for c1)")
     p.add_argument("--dry-run", action="store_true",
@@ -467,6 +478,23 @@ def make_loop(M, torch, cfg, pool, comm):
     return loop, x
 
 
+def dump_outputs(path, torch, cfg, repochs, x, recv):
+    """--dump-outputs: what the timed loop's caller holds after its last step, as <name>.npy:
+    `x` the iterate, `recvbuf` the workers' gathered gradients (n partitions), `repochs` the
+    epoch of each partition.  float64 for an fp64 config, else float32 (the bf16 config's
+    master iterate and gradients are fp32); a few KiB to 4 MiB, so nothing is sampled.  The
+    inputs are a function of --seed and the config alone and x starts at 0, so a run with
+    nwait = n (c2, the default) repeats its outputs up to the order of the kernel's float
+    atomics; with nwait < n the set of fresh workers depends on timing."""
+    np_dt = np.float64 if cfg["dtype"] == "f64" else np.float32
+    torch.cuda.synchronize()
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "x.npy"), x.detach().cpu().numpy().astype(np_dt))
+    np.save(os.path.join(path, "recvbuf.npy"), recv.detach().cpu().numpy().astype(np_dt))
+    np.save(os.path.join(path, "repochs.npy"), np.asarray(repochs, dtype=np.float64))
+    progress("outputs written to %s" % path)
+
+
 def run_single(args, cfg):
     import torch
     import mpiasyncpools as M
@@ -494,7 +522,7 @@ def run_single(args, cfg):
     loop, x = make_loop(M, torch, cfg, pool, comm)
     _, recv, isend, irecv = loop.bufs
     extra = {}
-    if cfg["config"] in ("c1", "c2"):
+    if args.full and cfg["config"] in ("c1", "c2"):
         # the same loop from Python (asyncmap_ + weights + lsq_update per step), reported beside:
         # what a caller driving asyncmap! itself per epoch (the reference's own loop) sees
         w = np.zeros(n)
@@ -534,6 +562,8 @@ def run_single(args, cfg):
     extra["launches_total"] = comm.counter("task_launches") - launches0  # timed or not
     extra["exchange"] = exchange_report(comm.exchange_timing())
     fresh = int((pool.repochs == pool.epoch).sum())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, torch, cfg, pool.repochs, x, recv)
     # launches after the timed region (waitall releases held stale re-dispatches): counted, so
     # that a kernel trace of this command can drop them from its timed-region window
     # (tools/trace_window.py)
@@ -543,22 +573,23 @@ def run_single(args, cfg):
     extra["launches_after_timed"] = comm.counter("task_launches") - l_end
     comm.timing()
     comm.set_timing(False)
-    extra["measured_read_peak"] = read_peak(M, torch)
-    if timing[0] and timing[2] / timing[0] < 3.5e9:
+    if args.full:
+        extra["measured_read_peak"] = read_peak(M, torch)
+    if args.full and timing[0] and timing[2] / timing[0] < 3.5e9:
         # a launch smaller than the 4 GiB probe (the per-GPU shares c2n2 / c2n4 / c2n8): the
         # same read at that size, whose ramp and tail weigh as they do in the launch
         extra["measured_read_peak_launch_bytes"] = read_peak(M, torch, timing[2] / timing[0] // 4096 * 4096)
     extra.update({"x_norm": float(torch.linalg.norm(x.float()).item()), "build": M.lib().mpa_build_info().decode(),
                   "loop": "native coordinator loop (mpa_lsq%s_descent)" % ("b" if batched else ""),
                   "fresh_at_last_epoch": fresh})
-    if cfg["config"] == "c2":
+    if args.full and cfg["config"] == "c2":
         extra["loop"] += "; python loop beside it"
-    # the CPU beside the device: c2 threaded (the bench's headline config), c1 as the reference
-    # runs configs[0] (coordinator + worker processes over MPI)
+    # the CPU beside the device (--full): c2 threaded (the bench's headline config), c1 as the
+    # reference runs configs[0] (coordinator + worker processes over MPI)
     extra["cpu_baseline"] = None
-    if not args.no_cpu_baseline and cfg["config"] == "c2":
+    if args.full and not args.no_cpu_baseline and cfg["config"] == "c2":
         extra["cpu_baseline"] = cpu_baseline(cfg, args.cpu_seconds)
-    elif not args.no_cpu_baseline and cfg["config"] == "c1":
+    elif args.full and not args.no_cpu_baseline and cfg["config"] == "c1":
         extra["cpu_baseline"] = mpi_baseline(cfg, args.cpu_seconds)
     print(json.dumps(report(args, cfg, 1, el, [timing], extra)), flush=True)
     comm.shutdown()
@@ -616,8 +647,13 @@ def run_multi(args, cfg, rank, world, local):
         torch.cuda.synchronize()
         el = time.perf_counter() - t0
         fresh = int((pool.repochs == pool.epoch).sum())
+        # --dump-outputs: device copies now (the other ranks' timed session lasts until the
+        # shutdown below), written once the ranks are released
+        held = (x.clone(), recv.clone(), pool.repochs.copy()) if args.dump_outputs else None
         M.waitall_(pool, recv, irecv)
         comm.shutdown()
+        if held:
+            dump_outputs(args.dump_outputs, torch, cfg, held[2], held[0], held[1])
     else:
         comm.serve()  # timed session, returns at shutdown
         torch.cuda.synchronize()

@@ -6,6 +6,8 @@ import argparse
 import os
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
@@ -183,3 +185,39 @@ def test_c5_reports_its_matrix_core_side():
     assert m["peak_TFLOPs"] == 2500.0 and abs(m["frac_issued"] - 1.5 * alg_tf / 2500.0) < 1e-3
     assert abs(r["frac"] - 8 * task / 7.45e-3 / 1e9 / 8000.0) < 1e-3
     assert "mfma" not in bench.report(_args(), _cfg("c2"), 1, 0.1, [(100, 60.0, 100 * 4299227136.0, 60.0)], {})["roofline"]
+
+
+def test_plain_run_is_the_default_and_full_is_an_option(monkeypatch):
+    """`bench.py --gpus 1 --steps K --warmup W` is the lean run; --full and --dump-outputs are
+    off unless asked for."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "out"
+
+
+@pytest.mark.parametrize("config,np_dtype", [("c2", "float32"), ("c1", "float64"), ("c5", "float32")])
+def test_dump_outputs_writes_npy(tmp_path, config, np_dtype):
+    """--dump-outputs: x, recvbuf and repochs as .npy, float64 for the fp64 config and float32
+    otherwise, values unchanged (host tensors stand in for the device's here)."""
+    import types
+
+    import numpy as np
+    import torch
+    cfg = _cfg(config)
+    n, cols, k = cfg["workers"], cfg["cols"], cfg.get("iterates", 1)
+    dt = torch.float64 if cfg["dtype"] == "f64" else torch.float32  # c5's iterate and gradients are fp32
+    g = torch.Generator().manual_seed(3)
+    x = torch.rand(cols * k, generator=g, dtype=dt)
+    recv = torch.rand(n * cols * k, generator=g, dtype=dt)
+    repochs = np.arange(1, n + 1, dtype=np.int64)
+    host = types.SimpleNamespace(cuda=types.SimpleNamespace(synchronize=lambda: None))
+    out = tmp_path / "deep" / "dir"
+    bench.dump_outputs(str(out), host, cfg, repochs, x, recv)
+    assert sorted(p.name for p in out.iterdir()) == ["recvbuf.npy", "repochs.npy", "x.npy"]
+    gx, gr, ge = (np.load(out / f) for f in ("x.npy", "recvbuf.npy", "repochs.npy"))
+    assert gx.dtype == np.dtype(np_dtype) and gr.dtype == np.dtype(np_dtype) and ge.dtype == np.float64
+    assert np.array_equal(gx, x.numpy()) and np.array_equal(gr, recv.numpy()) and ge.tolist() == repochs.tolist()
+    assert sum(p.stat().st_size for p in out.iterdir()) <= 64 << 20

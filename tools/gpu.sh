@@ -11,7 +11,7 @@
 #
 #   smoke                        __graft_entry__.smoke()
 #   tests[:EXPR]                 the -m gpu suite (pytest -k EXPR), verbose, per-test timeout
-#   bench:CFG[:ARGS]             python bench.py --config CFG ARGS -> bench_CFG.json
+#   bench:CFG[:ARGS]             python bench.py --full --config CFG ARGS -> bench_CFG.json
 #   trace:CFG[:ARGS]             rocprofv3 --kernel-trace --stats of that bench -> trace_CFG/
 #   pmc:CFG:CTRS[:ARGS]          one rocprofv3 --pmc pass (CTRS comma-separated) -> pmc_CFG_<n>/
 #   ab:CFG:REPS:LIB[:ARGS]       REPS alternations: product library, then MPA_LIB=LIB (A/B on one box)
@@ -48,7 +48,7 @@ run_step() {
       grep -E "^(FAILED|ERROR)|passed|failed" "$O/tests${TESTS_TAG:-}.log" | tail -5
       return $rc ;;
     bench)
-      timeout -k 10 600 python -u bench.py --config "$a" ${b//+/ } > "$O/bench_$a.log" 2>&1 || { r=$?; tail -20 "$O/bench_$a.log"; return $r; }
+      timeout -k 10 600 python -u bench.py --full --config "$a" ${b//+/ } > "$O/bench_$a.log" 2>&1 || { r=$?; tail -20 "$O/bench_$a.log"; return $r; }
       json_of "$O/bench_$a.log" "$O/bench_$a.json" ;;
     trace)
       (cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/trace_$a" -o "$a" -- python3 "$R/bench.py" --config "$a" --no-cpu-baseline ${b//+/ } > "$O/trace_$a.log" 2>&1) || { r=$?; tail -20 "$O/trace_$a.log"; return $r; }
