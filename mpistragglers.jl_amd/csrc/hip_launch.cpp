@@ -199,38 +199,13 @@ void HipComm::prepare_lsqb(int64_t rank, const TaskSpec& ts) {
     HIPCHECK(hipMemset(w.lsqb_ctr, 0, sizeof(uint32_t) * (kLsqbMaxSlices + 1)));
     HIPCHECK(hipDeviceSynchronize());
   }
-  if (ts.cols <= kLsqpMaxCols && !w.lsqp_slab) {  // lsqp4 (and the measurement build's lsqp / lsqc)
+  if (ts.cols <= kLsqpMaxCols && !w.lsqp_slab) {  // lsqp4
     HIPCHECK(hipMalloc(&w.lsqp_slab, size_t(2) * kLsqpMaxGroups * 8 * 32 * 1024));
-    const size_t nctr = size_t(2) * 8 * kLsqpCtrPerSlice + 8;  // + completions, lsqc ticket at +4
+    // tree counters, then the slice-completion word at [2 * 8 * kLsqpCtrPerSlice] (the highest
+    // index lsqp4_kernel and lsqp4_reduce_kernel touch)
+    const size_t nctr = size_t(2) * 8 * kLsqpCtrPerSlice + 1;
     HIPCHECK(hipMalloc(reinterpret_cast<void**>(&w.lsqp_ctr), sizeof(uint32_t) * nctr));
     HIPCHECK(hipMemset(w.lsqp_ctr, 0, sizeof(uint32_t) * nctr));
-    // the column pairs' exchange ring (measurement build) is rewritten every kLsqcXR blocks:
-    // in coarse-grained memory a reader's XCD L2 keeps serving its stale copy of a slot (sc1
-    // loads bypass only L1), so the granules live in uncached device memory
-    // (MPA_LSQC_XG=fine / coarse: A/B)
-    if (MPA_MEASURE) {
-      const size_t xg = size_t(kLsqpMaxGroups) * 2 * kLsqcXR * 4 * 64 * 4 * sizeof(unsigned long long);
-      const char* e = measure_env("MPA_LSQC_XG");
-      const unsigned fl = e && !std::strcmp(e, "fine") ? hipDeviceMallocFinegrained : hipDeviceMallocUncached;
-      if (e && !std::strcmp(e, "coarse")) HIPCHECK(hipMalloc(reinterpret_cast<void**>(&w.lsqc_xg), xg));
-      else HIPCHECK(hipExtMallocWithFlags(reinterpret_cast<void**>(&w.lsqc_xg), xg, fl));
-      HIPCHECK(hipMemset(w.lsqc_xg, 0, xg));
-    }
-    HIPCHECK(hipDeviceSynchronize());
-  }
-  if (!MPA_MEASURE) return;  // the probe kernels' scratch (lsqq, lsqf): measurement build only
-  if (ts.cols <= 2048 && !w.lsqq_ctr) {
-    HIPCHECK(hipMalloc(reinterpret_cast<void**>(&w.lsqq_ctr), sizeof(uint32_t) * 8));
-    HIPCHECK(hipMemset(w.lsqq_ctr, 0, sizeof(uint32_t) * 8));
-  }
-  if (ts.cols <= kLsqfMaxP * kLsqfSlice && !w.lsqf_x) {
-    const size_t slots = size_t(kLsqfMaxGroups) * kLsqfXR * kLsqfMaxP;
-    HIPCHECK(hipMalloc(&w.lsqf_x, slots * 4 * 64 * 16));
-    HIPCHECK(hipMalloc(reinterpret_cast<void**>(&w.lsqf_flag), slots * sizeof(unsigned long long)));
-    HIPCHECK(hipMemset(w.lsqf_flag, 0, slots * sizeof(unsigned long long)));
-    // 8 slice / completion counters, then at byte 64 the per-XCD and arrival ticket words
-    HIPCHECK(hipMalloc(reinterpret_cast<void**>(&w.lsqf_ctr), kLsqfCtrBytes));
-    HIPCHECK(hipMemset(w.lsqf_ctr, 0, kLsqfCtrBytes));
     HIPCHECK(hipDeviceSynchronize());
   }
 }
@@ -624,73 +599,6 @@ bool HipComm::lsqp_enabled(const std::vector<int64_t>& ranks) const {
   return !ranks.empty();
 }
 
-int HipComm::lsqc_groups(const TaskSpec& ts, int split, int k) const {
-  constexpr int target = 256;
-  const int per = target / split + (k < target % split ? 1 : 0);
-  const int64_t nblocks = (ts.rows + 15) / 16;
-  return int(std::max<int64_t>(1, std::min<int64_t>(std::min(per / lsqc_parts(ts.cols), kLsqpMaxGroups), nblocks)));
-}
-
-bool HipComm::lsqc_fits(const std::vector<int64_t>& ranks, const LsqpBatch& b, int share) const {
-  const int split = std::max(b.ntasks, share > 0 ? share : lsqb_share());
-  for (size_t k = 0; k < ranks.size(); ++k) {
-    const TaskSpec& ts = tasks_[size_t(ranks[k] - 1)];
-    const int64_t nblocks = (ts.rows + 15) / 16;
-    const int ng = lsqc_groups(ts, split, int(k));
-    if ((nblocks + ng - 1) / ng > kLsqcMaxBlocks || !w_[size_t(ranks[k] - 1)].lsqc_xg) return false;
-  }
-  return true;
-}
-
-void HipComm::build_lsqc(const std::vector<int64_t>& ranks, int share, LsqbLaunch& L) {
-  LsqpBatch& b = L.halves;
-  L.cpair = true;
-  const int split = std::max(b.ntasks, share > 0 ? share : lsqb_share());
-  int wgs = 0;
-  for (int k = 0; k < b.ntasks; ++k) {
-    const int64_t rank = ranks[size_t(k)];
-    const HipWorker& w = w_[size_t(rank - 1)];
-    const TaskSpec& ts = tasks_[size_t(rank - 1)];
-    LsqpTask& t = b.t[k];
-    t.xg = w.lsqc_xg;
-    t.parts = lsqc_parts(ts.cols);
-    b.grp0[k] = wgs;
-    wgs += lsqc_groups(ts, split, k) * t.parts;
-  }
-  b.grp0[b.ntasks] = wgs;
-  b.tick = w_[size_t(ranks[0] - 1)].lsqp_ctr + 2 * 8 * kLsqpCtrPerSlice + 4;
-  b.pfd = lsqc_la_;  // lsqc: the phase-1 lookahead
-  b.err = err_dev_;
-  b.spin_ticks = spin_ticks();
-}
-
-bool HipComm::lsqq_enabled(const std::vector<int64_t>& ranks) const {
-  if (!MPA_MEASURE) return false;  // a probe kernel of the measurement build (make MEASURE=1)
-  const char* e = measure_env("MPA_LSQQ");
-  if (!e || *e != '1') return false;
-  for (int64_t rank : ranks) {
-    const TaskSpec& ts = tasks_[size_t(rank - 1)];
-    if (!w_[size_t(rank - 1)].lsqq_ctr || ts.cols > 2048) return false;
-  }
-  return !ranks.empty();
-}
-
-bool HipComm::lsqf_enabled(const std::vector<int64_t>& ranks) const {
-  // measurement build, opt-in: the single-pass kernel is correct but, as measured
-  // (DESIGN.md §10), slower than the two passes
-  const char* e = measure_env("MPA_LSQF");
-  if (!e || *e != '1') return false;
-  int P = 0;
-  for (int64_t rank : ranks) {
-    const TaskSpec& ts = tasks_[size_t(rank - 1)];
-    const HipWorker& w = w_[size_t(rank - 1)];
-    const int p = int((ts.cols + kLsqfSlice - 1) / kLsqfSlice);
-    if (!w.lsqf_x || p > kLsqfMaxP || (P && p != P)) return false;
-    P = p;
-  }
-  return P > 0;
-}
-
 int HipComm::lsqb_share() const {
   if (!lsqp_share_) return 1;
   int k = 0;
@@ -708,15 +616,26 @@ HipComm::LsqbLaunch HipComm::build_lsqb_batch(const std::vector<int64_t>& ranks,
              2.0 * double(ts.cols) * double(ts.k) + 4.0 * double(ts.cols) * double(ts.k);
   }
   *bytes_out = bytes;
-  if (lsqp_enabled(ranks) && !lsqf_enabled(ranks) && !lsqq_enabled(ranks)) {
+  // what a task of either kernel takes from the worker and its registration
+  auto fill = [&](auto& t, const HipWorker& w, const TaskSpec& ts) {
+    t.A = ts.A;
+    t.B = ts.b;
+    t.X = w.x;
+    t.out = w.out;
+    t.flag = w.flag_dev;
+    t.flag2 = peer_done(w);
+    t.seq = w.seq;
+    t.rows = ts.rows;
+    t.lda = ts.lda;
+    t.cols = int(ts.cols);
+  };
+  if (lsqp_enabled(ranks)) {
     L.pair = true;
-    L.pair8 = lsqp8_;
     LsqpBatch& b = L.halves;
     b.ntasks = int(ranks.size());
     b.err = err_dev_;  // the device-armed doorbell wait's error word and bound
     b.spin_ticks = spin_ticks();
-    b.pfd = lsqp_pfd_ >= 0 ? lsqp_pfd_ : (lsqp8_ ? 0 : 1);
-    { const char* d = measure_env("MPA_LSQP_DBG"); b.dbg = d ? std::atoi(d) : 0; }
+    b.pfd = lsqp_pfd_ >= 0 ? lsqp_pfd_ : 1;
     // one workgroup per CU: 128 pairs (256 workgroups), dealt evenly over max(tasks,
     // share) tasks; 120 (240) where the task streams leave one CU per XCD to the coordinator
     // (reserve_cus_: 31 CUs per XCD, a pair's two members on one XCD)
@@ -728,18 +647,9 @@ HipComm::LsqbLaunch HipComm::build_lsqb_batch(const std::vector<int64_t>& ranks,
       HipWorker& w = w_[size_t(rank - 1)];
       const TaskSpec& ts = tasks_[size_t(rank - 1)];
       LsqpTask& t = b.t[k];
-      t.A = ts.A;
-      t.B = ts.b;
-      t.X = w.x;
-      t.out = w.out;
+      fill(t, w, ts);
       t.slab = w.lsqp_slab;
       t.ctr = w.lsqp_ctr;
-      t.flag = w.flag_dev;
-      t.flag2 = peer_done(w);
-      t.seq = w.seq;
-      t.rows = ts.rows;
-      t.lda = ts.lda;
-      t.cols = int(ts.cols);
       t.pub_local = pub_local();
       const int per = target / split + (k < target % split ? 1 : 0);
       const int64_t nblocks = (ts.rows + 15) / 16;
@@ -748,89 +658,6 @@ HipComm::LsqbLaunch HipComm::build_lsqb_batch(const std::vector<int64_t>& ranks,
       pairs += ng;
     }
     b.grp0[b.ntasks] = pairs;
-    if (lsqc_ && lsqc_fits(ranks, b, share)) build_lsqc(ranks, share, L);
-    return L;
-  }
-  if (lsqq_enabled(ranks)) {
-    L.quad = true;
-    LsqqBatch& b = L.four;
-    b.ntasks = int(ranks.size());
-    { const char* d = measure_env("MPA_LSQQ_DBG"); b.dbg = d ? std::atoi(d) : 0; }
-    // one 512-thread workgroup per CU: 64 quads (grid 256, a multiple of 32 so that each
-    // quad's members share an XCD), dealt evenly over the tasks
-    constexpr int target = 64;
-    int groups = 0;
-    for (int k = 0; k < b.ntasks; ++k) {
-      const int64_t rank = ranks[size_t(k)];
-      HipWorker& w = w_[size_t(rank - 1)];
-      const TaskSpec& ts = tasks_[size_t(rank - 1)];
-      LsqqTask& t = b.t[k];
-      t.A = ts.A;
-      t.B = ts.b;
-      t.X = w.x;
-      t.out = w.out;
-      t.slab = w.lsqb_slab;
-      t.ctr = w.lsqq_ctr;
-      t.flag = w.flag_dev;
-      t.seq = w.seq;
-      t.rows = ts.rows;
-      t.lda = ts.lda;
-      t.cols = int(ts.cols);
-      const int per = target / b.ntasks + (k < target % b.ntasks ? 1 : 0);
-      const int64_t nblocks = (ts.rows + 15) / 16;
-      const int ng = int(std::max<int64_t>(1, std::min<int64_t>(std::min(per, kLsqfMaxGroups), nblocks)));
-      b.grp0[k] = groups;
-      groups += ng;
-    }
-    b.grp0[b.ntasks] = groups;
-    return L;
-  }
-  if (lsqf_enabled(ranks)) {
-    L.fused = true;
-    LsqfBatch& b = L.one;
-    b.ntasks = int(ranks.size());
-    b.err = err_dev_;
-    b.spin_ticks = spin_ticks();
-    // probe modes and the phase-1 lead: measurement build only (make MEASURE=1)
-    { const char* d = measure_env("MPA_LSQF_DBG"); b.dbg = d ? std::atoi(d) : 0; }
-    { const char* d = measure_env("MPA_LSQF_LAG"); b.lag = d ? std::atoi(d) : 4; }
-    b.P = int((tasks_[size_t(ranks[0] - 1)].cols + kLsqfSlice - 1) / kLsqfSlice);
-    // one workgroup per CU: groups of P, as many as keep the grid a multiple of 8 P (the
-    // groups form inside an XCD, 8 XCDs), dealt evenly over the tasks
-    const int target = std::max(1, (kLsqfGrid / b.P) / 8 * 8);
-    HipWorker& w0 = w_[size_t(ranks[0] - 1)];
-    b.tick = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(w0.lsqf_ctr) + 64);
-    b.tag = uint32_t(w0.seq);
-    int groups = 0;
-    for (int k = 0; k < b.ntasks; ++k) {
-      const int64_t rank = ranks[size_t(k)];
-      HipWorker& w = w_[size_t(rank - 1)];
-      const TaskSpec& ts = tasks_[size_t(rank - 1)];
-      LsqfTask& t = b.t[k];
-      t.A = ts.A;
-      t.B = ts.b;
-      t.X = w.x;
-      t.out = w.out;
-      t.xbuf = w.lsqf_x;
-      t.xflag = w.lsqf_flag;
-      t.slab = w.lsqb_slab;
-      t.ctr = w.lsqf_ctr;
-      t.flag = w.flag_dev;
-      t.seq = w.seq;
-      t.rows = ts.rows;
-      t.lda = ts.lda;
-      t.cols = int(ts.cols);
-      const int64_t nblocks = (ts.rows + 15) / 16;
-      const int per = target / b.ntasks + (k < target % b.ntasks ? 1 : 0);
-      const int ng = int(std::max<int64_t>(1, std::min<int64_t>(std::min(per, kLsqfMaxGroups), nblocks)));
-      t.sbase = w.lsqf_sbase;
-      t.tbase = w.lsqf_tbase;
-      w.lsqf_sbase += uint32_t(ng);
-      w.lsqf_tbase += uint32_t(b.P);
-      b.grp0[k] = groups;
-      groups += ng;
-    }
-    b.grp0[b.ntasks] = groups;
     return L;
   }
   LsqbBatch& b = L.two;
@@ -847,19 +674,10 @@ HipComm::LsqbLaunch HipComm::build_lsqb_batch(const std::vector<int64_t>& ranks,
     HipWorker& w = w_[size_t(rank - 1)];
     const TaskSpec& ts = tasks_[size_t(rank - 1)];
     LsqbTask& t = b.t[k];
-    t.A = ts.A;
-    t.B = ts.b;
-    t.X = w.x;
-    t.out = w.out;
+    fill(t, w, ts);
     t.R = w.lsqb_R;
     t.slab = w.lsqb_slab;
     t.ctr = w.lsqb_ctr;
-    t.flag = w.flag_dev;
-    t.flag2 = peer_done(w);
-    t.seq = w.seq;
-    t.rows = ts.rows;
-    t.lda = ts.lda;
-    t.cols = int(ts.cols);
     const int64_t nblocks = b.splitk ? ((ts.rows + 31) / 32) * (32 / kLsqbSplitKRows) : (ts.rows + 255) / 256;
     t.grid1 = int(std::max<int64_t>(1, std::min<int64_t>(nblocks, per1)));
     t.nslice = int((ts.cols + 255) / 256);
@@ -894,13 +712,7 @@ void HipComm::enqueue_lsqb(const LsqbLaunch& b, hipStream_t s, double bytes, int
     tl.rank = armed_rank;
     HIPCHECK(hipEventRecord(tl.start, s));
   }
-#if MPA_MEASURE
-  HIPCHECK(b.pair ? (b.cpair ? launch_lsqc(b.halves, s) : b.pair8 ? launch_lsqp(b.halves, s) : launch_lsqp4(b.halves, s))
-                  : b.quad ? launch_lsqq(b.four, s) : b.fused ? launch_lsqf(b.one, s) : launch_lsqb(b.two, s));
-#else
-  // the product carries the iterate-halves single pass and the two passes only
   HIPCHECK(b.pair ? launch_lsqp4(b.halves, s) : launch_lsqb(b.two, s));
-#endif
   if (timed) {
     HIPCHECK(hipEventRecord(tl.stop, s));
     std::lock_guard<std::mutex> lk(tm_mu_);

@@ -150,8 +150,6 @@ void HipComm::arm(int64_t rank) {
   const int par = int(s & 1);
   w.arm_sbase[par] = w.lsqb_sbase;
   w.arm_tbase[par] = w.lsqb_tbase;
-  w.arm_fsbase[par] = w.lsqf_sbase;
-  w.arm_ftbase[par] = w.lsqf_tbase;
   w.seq = s;
   unsigned long long* cancel = w.cancel_dev + par;
   w.sl = task_msg_bytes(ts);
@@ -213,8 +211,6 @@ void HipComm::disarm_all() {
       const int par = int((ran + 1) & 1);
       w.lsqb_sbase = w.arm_sbase[par];
       w.lsqb_tbase = w.arm_tbase[par];
-      w.lsqf_sbase = w.arm_fsbase[par];
-      w.lsqf_tbase = w.arm_ftbase[par];
       for (unsigned long long s = ran + 1; s <= newest; ++s) void_timing(r);
       w.seq = ran;
     }

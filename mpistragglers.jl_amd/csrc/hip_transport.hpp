@@ -78,8 +78,6 @@ constexpr int64_t kClockRateSpanNs = 1000000000;
 constexpr int kLsqbGrid1 = 512;  // two 8-wave workgroups per CU: pass 1 4.74-4.88 -> 5.11 TB/s (profiles/r01_lsqb_grid.txt)
 constexpr int kLsqbGrid2 = 512;
 constexpr int kLsqbRangeCap = 128;
-constexpr int kLsqfGrid = 256;  // single-pass batched launch: one 768-thread workgroup per CU
-constexpr size_t kLsqfCtrBytes = 64 + 16 * sizeof(unsigned long long);
 
 inline bool env_off(const char* name) {
   const char* e = std::getenv(name);
@@ -126,17 +124,9 @@ struct HipWorker {
   size_t lsqb_slab_bytes = 0;
   uint32_t* lsqb_ctr = nullptr;
   uint32_t lsqb_sbase = 0, lsqb_tbase = 0;
-  // single-pass variant (lsqf_kernel.hip): exchange ring, its flags, counters
-  // ([kLsqfMaxP] slices, [1] completions, [1] group tickets) and their running totals
-  void* lsqf_x = nullptr;
-  unsigned long long* lsqf_flag = nullptr;
-  uint32_t* lsqf_ctr = nullptr;
-  uint32_t* lsqq_ctr = nullptr;  // quad kernel: [4] member arrivals, [4] completions (self-resetting)
-  // pair single pass (lsqp_kernel.hip): G partials and tree counters (self-resetting)
+  // single pass by iterate halves (lsqp4_kernel.hip): G partials and tree counters (self-resetting)
   void* lsqp_slab = nullptr;
-  uint32_t* lsqp_ctr = nullptr;  // [2][8][kLsqpCtrPerSlice] tree, [1] completions, then the lsqc ticket
-  unsigned long long* lsqc_xg = nullptr;  // column pairs: exchange granules
-  uint32_t lsqf_sbase = 0, lsqf_tbase = 0;
+  uint32_t* lsqp_ctr = nullptr;  // LsqpTask::ctr
   // current task
   int64_t slot = -1;
   const uint8_t* x = nullptr;
@@ -165,7 +155,7 @@ struct HipWorker {
   unsigned long long* cancel_dev = nullptr;
   // coordinator, launch-ahead: the next post / harvest of this worker is already enqueued
   bool preposted = false, preharvest = false;
-  uint32_t arm_sbase[2] = {0, 0}, arm_tbase[2] = {0, 0}, arm_fsbase[2] = {0, 0}, arm_ftbase[2] = {0, 0};
+  uint32_t arm_sbase[2] = {0, 0}, arm_tbase[2] = {0, 0};
   int64_t tslot = -1;  // task trace (mpa_comm_set_trace): the current task's entry, -1 none
 };
 
@@ -644,50 +634,27 @@ class HipComm final : public Comm {
     enqueue_lsqb(b, s, bytes);
   }
 
-  // A batched multi-iterate launch: the single-pass kernel (lsqf_kernel.hip) where every
-  // task of the batch has the same slice count (cols <= 2048) and MPA_LSQF is not 0, else
-  // the two passes (lsqb_kernel.hip).
+  // A batched multi-iterate launch: the single pass by iterate halves (lsqp4_kernel.hip) where
+  // every task of the batch has cols <= 2048 and MPA_LSQP is not 0, else the two passes
+  // (lsqb_kernel.hip).
   struct LsqbLaunch {
-    bool pair = false;   // lsqp (the default single pass)
-    bool pair8 = false;  // ... by the eight-wave cut (MPA_LSQP=8)
-    bool cpair = false;  // ... by column pairs (lsqc_kernel.hip)
-    bool fused = false;  // lsqf (opt-in)
-    bool quad = false;   // lsqq
+    bool pair = false;  // the single pass (`halves`), else the two passes (`two`)
     LsqbBatch two{};
-    LsqfBatch one{};
-    LsqqBatch four{};
     LsqpBatch halves{};
     void set_go(const unsigned long long* go) {
       if (pair) halves.t[0].go = go;
-      else if (quad) four.t[0].go = go;
-      else if (fused) one.t[0].go = go;
       else two.t[0].go = go;
     }
-    // device-armed launches: the product's kernels (lsqp4, the two passes) only
+    // device-armed launch
     void set_door(const unsigned long long* door) {
-      if (pair && !pair8 && !cpair) halves.t[0].door = door;
-      else if (!pair && !quad && !fused) two.t[0].door = door;
-      else fail(MPA_ERROR, "device-armed tasks run the product's batched kernels only");
+      if (pair) halves.t[0].door = door;
+      else two.t[0].door = door;
     }
   };
 
-  // the iterate-halves single pass (lsqp_kernel.hip): the default for cols <= 2048
+  // the iterate-halves single pass (lsqp4_kernel.hip): the default for cols <= 2048
   // (MPA_LSQP=0 selects the two passes)
   bool lsqp_enabled(const std::vector<int64_t>& ranks) const;
-
-  // column pairs (lsqc_kernel.hip): a row group of a task with more than 1024 columns is a
-  // pair of workgroups (one each, 1024 columns and all 64 iterates), of a narrower task one
-  // workgroup; 256 workgroups (one per CU) dealt over the tasks.  Row groups of at most
-  // kLsqcMaxBlocks blocks (the tag's block field), else the iterate-halves kernel stays.
-  static int lsqc_parts(int64_t cols) { return cols > kLsqcMemberCols ? 2 : 1; }
-  int lsqc_groups(const TaskSpec& ts, int split, int k) const;
-  bool lsqc_fits(const std::vector<int64_t>& ranks, const LsqpBatch& b, int share) const;
-  void build_lsqc(const std::vector<int64_t>& ranks, int share, LsqbLaunch& L);
-
-  // the iterate-quarter single pass (lsqq_kernel.hip): cols <= 2048 on every task
-  bool lsqq_enabled(const std::vector<int64_t>& ranks) const;
-
-  bool lsqf_enabled(const std::vector<int64_t>& ranks) const;
 
   // kernel arguments over `ranks`; advances the workers' counter bases.  Algorithmic bytes
   // per task: A + B + X + G.
@@ -844,12 +811,8 @@ class HipComm final : public Comm {
   std::vector<int64_t> held_;  // held re-dispatches, launched with the next batch
   // held re-dispatches: held, later joined a batched launch, launched on their own
   int64_t n_held_ = 0, n_held_joined_ = 0, n_held_alone_ = 0;
-  bool lsqp8_ = false;  // MPA_LSQP=8: the eight-wave single pass (lsqp_kernel.hip)
-  bool lsqc_ = false;   // MPA_LSQP=c: the column-pair single pass (lsqc_kernel.hip)
-  int lsqc_la_ = 2;     // MPA_LSQC_LA: its phase-1 lookahead in blocks (2; 1 for A/B)
-  // lsqp L2 prefetch lead in blocks (MPA_LSQP_PF; 0 = off; unset: 1 for lsqp4, 0 for the
-  // eight-wave cut).  lsqp4: 1 block 8.47 ms vs 9.50 without, 2-4 slower (L2 thrash);
-  // profiles/r02_c5_lsqp_tuning.txt
+  // lsqp4 L2 prefetch lead in blocks (MPA_LSQP_PF; 0 = off; unset: 1).  1 block 8.47 ms vs
+  // 9.50 without, 2-4 slower (L2 thrash); profiles/r02_c5_lsqp_tuning.txt
   int lsqp_pfd_ = -1;
   bool tail_next_ = false, tail_pending_ = false;
   // fused head (flush): the next least-squares launch runs this epoch's step first

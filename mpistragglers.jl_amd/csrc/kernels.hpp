@@ -251,21 +251,22 @@ struct LsqbBatch {
 // pass 1 + pass 2 of every task of the batch, two launches on `s`
 hipError_t launch_lsqb(const LsqbBatch& a, hipStream_t s);
 
-// Single pass by iterate halves (lsqp_kernel.hip, the c5 default for cols <= 2048): pairs of
-// workgroups stream the same rows, member h owning iterates 32h .. 32h + 31 of R and G; no
-// exchange between members.  Pairs [grp0[t], grp0[t+1]) serve task t (grid = 16 x ceil(pairs
-// / 8): the members of pair p are blocks 16 (p / 8) + p % 8 and that + 8).
+// Single pass by iterate halves (lsqp4_kernel.hip, the c5 default for cols <= 2048): pairs of
+// workgroups, four waves each (one per SIMD, 512 columns a wave), stream the same rows, member h
+// owning iterates 32h .. 32h + 31 of R and G; no exchange between members.  Pairs [grp0[t],
+// grp0[t+1]) serve task t (grid = 16 x ceil(pairs / 8): the members of pair p are blocks
+// 16 (p / 8) + p % 8 and that + 8, one XCD under round-robin placement).
 constexpr int kLsqpMaxGroups = 128;   // pairs (row groups) per task
 constexpr int kLsqpCtrPerSlice = 64;  // tree counters per (half, wave): 32 + 8 + 2 + 1, rounded up
-constexpr int kLsqpMaxCols = 2048;    // 8 waves x 256 columns
+constexpr int kLsqpMaxCols = 2048;    // 4 waves x 512 columns
 struct LsqpTask {
   const void* A;
   const void* B;
   const void* X;
   void* out;
-  void* slab;      // [2][kLsqpMaxGroups][8 waves][32 KiB] fp32 G partials (tree reduced in place)
-  uint32_t* ctr;   // [2 halves][8 waves][kLsqpCtrPerSlice] tree counters + [1] slice completions;
-                   // every counter is reset by its last arriver
+  void* slab;      // [2][kLsqpMaxGroups][4 waves][64 KiB] fp32 G partials (tree reduced in place)
+  uint32_t* ctr;   // tree counters, [kLsqpCtrPerSlice] per (half h, wave w) at slice 4h + w, and the
+                   // slice-completion word at [2 * 8 * kLsqpCtrPerSlice]; each reset by its last arriver
   unsigned long long* flag;
   unsigned long long* flag2;  // N > 1, a worker process's task: rank 0's device copy of the done word, or null
   unsigned long long seq;
@@ -273,99 +274,22 @@ struct LsqpTask {
   int cols;
   const unsigned long long* go;  // as LsqTask::go
   const unsigned long long* door;  // as LsqTask::door
-  // column pairs (lsqc_kernel.hip) only
-  unsigned long long* xg;  // [kLsqpMaxGroups][2][kLsqcXR][4][64][4] {tag, fp32} exchange granules
-  int parts;               // members per row group: 2 if cols > kLsqcMemberCols, else 1
-  int pub_local;  // as LsqTask::pub_local (lsqp4)
+  int pub_local;  // as LsqTask::pub_local
 };
 struct LsqpBatch {
   int ntasks;
-  int pfd;  // L2 prefetch lead over the LDS-DMA, in blocks (0: none); MPA_LSQP_PF.  lsqc: phase-1 lookahead (1, 2)
-  int dbg;  // measurement build only (MPA_LSQP_DBG): 1 no DMA, 2 no compute, 8/16/32 no phase 1 / reduce / phase 2
-  int xred;  // lsqp4: G over the row groups in a second launch (set by launch_lsqp4; MPA_LSQP4_XRED=0: in-kernel tree)
-  int grp0[kMaxLsqTasks + 1];  // lsqp/lsqp4: pairs before task t; lsqc: workgroups before task t
+  int pfd;  // L2 prefetch lead over the LDS-DMA, in blocks (0: none); MPA_LSQP_PF
+  int xred;  // G over the row groups in a second launch (set by launch_lsqp4; MPA_LSQP4_XRED=0: in-kernel tree)
+  int grp0[kMaxLsqTasks + 1];  // pairs before task t
   LsqpTask t[kMaxLsqTasks];
-  // column pairs (lsqc_kernel.hip) only
-  uint32_t* tick;  // workgroup ticket counter (zero between launches: the last taker resets it)
-  // bounded in-kernel waits (lsqc's exchange, a device-armed task's doorbell): error word, bound
+  // a device-armed task's bounded doorbell wait: error word, bound
   unsigned* err;
   unsigned long long spin_ticks;
 };
-hipError_t launch_lsqp(const LsqpBatch& a, hipStream_t s);
-// the same batch by the one-wave-per-SIMD cut (lsqp4_kernel.hip, the default)
 hipError_t launch_lsqp4(const LsqpBatch& a, hipStream_t s);
 // (rounds 4-5 measured three more restructurings of lsqp4 -- phase 2 as 32x32x16 MFMAs, the
 // block-pipelined kernel, the pair step -- parity-green and level with it on HBM; removed in round
 // 6, their record is DESIGN.md §10 and profiles/r04_c5_*, r05_c5_pairstep.txt)
-// Single pass by COLUMN pairs (lsqc_kernel.hip): the two members of a row group split the
-// columns (member h: columns 1024 h .. 1024 h + 1023), each holding all 64 iterates of its G
-// columns, and exchange their 16 x 64 partial products per 16-row block as tagged granules.
-// Pairs form from a ticket taken at start (members only wait for running workgroups).
-constexpr int kLsqcMemberCols = 1024;
-constexpr int kLsqcXR = 8;           // exchange ring slots per member
-constexpr int kLsqcMaxBlocks = 65535;  // 16-row blocks per row group (16-bit block field of the tag)
-hipError_t launch_lsqc(const LsqpBatch& a, hipStream_t s);
-
-// Single-pass variant (lsqf_kernel.hip): groups of P = ceil(cols / kLsqfSlice) workgroups,
-// one 512-column slice each, exchanging per-block partial residuals through `xbuf`.
-constexpr int kLsqfSlice = 512;
-constexpr int kLsqfMaxP = 4;         // cols <= 2048
-constexpr int kLsqfXR = 16;          // exchange ring slots per group
-constexpr int kLsqfMaxGroups = 64;   // per task
-struct LsqfTask {
-  const void* A;
-  const void* B;
-  const void* X;
-  void* out;
-  void* xbuf;                  // [groups][kLsqfXR][P][4][64] f32x4 partial tiles
-  unsigned long long* xflag;   // [groups][kLsqfXR][P]: (seq << 32) | (block + 1)
-  void* slab;                  // [groups][P][128 KiB] G partials
-  uint32_t* ctr;               // [kLsqfMaxP] per-slice group arrivals + [1] slice completions
-  unsigned long long* flag;
-  unsigned long long seq;
-  int64_t rows, lda;
-  int cols;
-  uint32_t sbase, tbase;       // ctr values before this launch
-  const unsigned long long* go;
-};
-struct LsqfBatch {
-  int ntasks;
-  int P;                       // members per group (every task of a batch alike)
-  unsigned* err;
-  unsigned long long spin_ticks;
-  unsigned long long* tick;    // [8] per-XCD tickets, [8] arrivals: (tag << 32) | count
-  uint32_t tag;                // this launch's tag (low half of task 0's seq)
-  int lag;                     // phase 1 runs this many blocks ahead (MPA_LSQF_LAG, 1-4)
-  int dbg;                     // MPA_LSQF_DBG: mode 3 loader only, 4 no exchange, 7 all groups cross-XCD; +16 wait profile
-  int grp0[kMaxLsqTasks + 1];  // groups [grp0[t], grp0[t+1]) serve task t
-  LsqfTask t[kMaxLsqTasks];
-};
-hipError_t launch_lsqf(const LsqfBatch& a, hipStream_t s);
-
-// Single pass by iterate quarters (lsqq_kernel.hip): quads of workgroups, member q owns
-// iterates 16q..16q+15 of G for all columns (cols <= 2048); no exchange between members.
-struct LsqqTask {
-  const void* A;
-  const void* B;
-  const void* X;
-  void* out;
-  void* slab;                  // [groups][4][ceil(cols/256)][16][64] f32x4 G partials
-  uint32_t* ctr;               // [4] per-member group arrivals, [4] member completions (self-resetting)
-  unsigned long long* flag;
-  unsigned long long seq;
-  int64_t rows, lda;
-  int cols;
-  const unsigned long long* go;
-};
-struct LsqqBatch {
-  int ntasks;
-  int dbg;                     // MPA_LSQQ_DBG timing probes (lsqq_kernel.hip)
-  int grp0[kMaxLsqTasks + 1];  // quads [grp0[t], grp0[t+1]) serve task t; grid = 4 x quads
-  LsqqTask t[kMaxLsqTasks];
-};
-hipError_t launch_lsqq(const LsqqBatch& a, hipStream_t s);
-size_t lsqf_lds_bytes();
-void lsqf_prof_dump();  // MPA_LSQF_DBG & 16: wait-cycle breakdown to stderr
 void head_stamp_reset();  // MPA_HEAD_STAMP=1 (measurement build): the fused-head launch stamps
 void head_stamp_dump();
 void lsqp4_clock_dump();  // MPA_LSQP4_CLOCK=1: lsqp4's in-kernel clock of its last launch to stderr

@@ -2,16 +2,24 @@
 // configs[4], "c5"):
 //     G_i = A_i^T (A_i X - B_i)      A_i rows x cols bf16, X cols x 64 bf16, B_i rows x 64 bf16
 // in the reference's compute slot (examples/iterative_example.jl:74 sleeps there), A read
-// from HBM once.  The pair scheme of lsqp_kernel.hip (two workgroups on one XCD stream the
-// same rows, member h owning iterates 32h .. 32h + 31; the second reader of a block finds it
-// in L2), re-cut for the register file.
+// from HBM once.
 //
-// Why one wave per SIMD.  The eight-wave cut (lsqp_kernel.hip) holds G (128 registers) and X
+// Why halves.  The fp32 accumulator of G (cols x 64 x 4 B = 512 KiB at 2048 columns) is a
+// whole CU's register file, so one workgroup cannot hold G while it streams full rows of A
+// (which the residual needs).  Split the 64 iterates instead: a PAIR of workgroups streams
+// the same rows, member h computing the residual and G for iterates 32h .. 32h + 31 only
+// (R_h = A X_h - B_h needs full rows of A but only half of X; G_h = A^T R_h needs only R_h).
+// No data moves between the members; the second to read a block of A finds it in the XCD's
+// L2 (the members of a pair are placed on one XCD and start together), so HBM sees A once
+// and the L2 -> CU stream twice (34.5 TB/s of L2 against 2 x ~7 TB/s).
+//
+// Why one wave per SIMD.  The first cut of the pair scheme, eight waves of 256 columns each
+// (removed; measured in profiles/r02_c5_lsqp_tuning.txt), holds G (128 registers) and X
 // (64) in a 256-register wave budget, so every LDS read of the block loop waits for itself
 // (lgkmcnt(0) between reads) and the loop runs at ~2.3 us per 16-row block whether A comes
-// from HBM or the Infinity Cache (profiles/r02_c5_lsqp_tuning.txt): issue-bound, not memory-
-// bound.  Four waves of 512 registers each (G 256 accumulation registers, X 128, 128 free for
-// the pipeline) let the reads of a phase run ahead of its MFMAs.
+// from HBM or the Infinity Cache: issue-bound, not memory-bound.  Four waves of 512 registers
+// each (G 256 accumulation registers, X 128, 128 free for the pipeline) let the reads of a
+// phase run ahead of its MFMAs.
 //
 // Workgroup = 4 waves, one per SIMD, one workgroup per CU.  Wave w owns columns 512 w ..
 // 512 w + 511 in both products:
@@ -140,9 +148,9 @@ __device__ __forceinline__ void lgkm_wait() {
 __device__ __forceinline__ void barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // LDS-DMA of one 1-KiB slice row: lane l's 16 B land at lds + 16 l.  Scalar base + 32-bit lane
-// offset (the saddr form).  Inline asm on purpose, as in lsqp_kernel.hip: the compiler would
-// guard every LDS read that may alias a DMA it knows of with vmcnt(0), waiting for the NEXT
-// block too; the kernel orders its reads itself (vmcnt per block).
+// offset (the saddr form).  Inline asm on purpose, as in the removed eight-wave cut: the
+// compiler would guard every LDS read that may alias a DMA it knows of with vmcnt(0), waiting
+// for the NEXT block too; the kernel orders its reads itself (vmcnt per block).
 __device__ __forceinline__ void dma_row(const void* sbase, uint32_t voff, void* lds) {
   const uint32_t l = __builtin_amdgcn_readfirstlane(uint32_t(reinterpret_cast<uintptr_t>(lds)));
   asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(l) : "memory");

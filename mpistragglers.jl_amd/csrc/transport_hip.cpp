@@ -211,13 +211,6 @@ HipComm::HipComm(int64_t n, const int* devices, const int* placement, int my_ran
   HIPCHECK(hipHostMalloc(reinterpret_cast<void**>(&pre_mb_), sizeof(PreMailbox), hipHostMallocCoherent | hipHostMallocMapped));
   std::memset(static_cast<void*>(pre_mb_), 0, sizeof(PreMailbox));
   { const char* e = measure_env("MPA_LSQP_SHARE"); lsqp_share_ = e && *e == '1'; }
-  {
-    const char* e = measure_env("MPA_LSQP");  // the product's MPA_LSQP=0 is read where it applies
-    lsqp8_ = e && *e == '8';
-    lsqc_ = e && *e == 'c';
-    const char* la = measure_env("MPA_LSQC_LA");
-    lsqc_la_ = la && *la == '1' ? 1 : 2;
-  }
   hold_ok_ = !env_off("MPA_HOLD");
   { const char* e = measure_env("MPA_GATHER"); batch_gather_ = !(e && *e == '0'); }
   if (const char* e = measure_env("MPA_LSQP_PF")) lsqp_pfd_ = std::max(0, std::min(8, std::atoi(e)));
@@ -244,7 +237,6 @@ HipComm::~HipComm() {
   stop_clock();
   (void)hipDeviceSynchronize();
 #if MPA_MEASURE
-  if (const char* d = measure_env("MPA_LSQF_DBG"); d && (std::atoi(d) & 16)) lsqf_prof_dump();
   if (const char* d = measure_env("MPA_LSQP4_CLOCK"); d && *d == '1') lsqp4_clock_dump();
   if (const char* d = measure_env("MPA_LSQ_STAMP"); d && *d == '1') lsq_stamp_dump();
   if (const char* d = measure_env("MPA_HEAD_STAMP"); d && *d == '1') head_stamp_dump();
@@ -255,13 +247,8 @@ HipComm::~HipComm() {
     if (w.lsqb_R) (void)hipFree(w.lsqb_R);
     if (w.lsqb_slab) (void)hipFree(w.lsqb_slab);
     if (w.lsqb_ctr) (void)hipFree(w.lsqb_ctr);
-    if (w.lsqf_x) (void)hipFree(w.lsqf_x);
-    if (w.lsqf_flag) (void)hipFree(w.lsqf_flag);
-    if (w.lsqf_ctr) (void)hipFree(w.lsqf_ctr);
-    if (w.lsqq_ctr) (void)hipFree(w.lsqq_ctr);
     if (w.lsqp_slab) (void)hipFree(w.lsqp_slab);
     if (w.lsqp_ctr) (void)hipFree(w.lsqp_ctr);
-    if (w.lsqc_xg) (void)hipFree(w.lsqc_xg);
     if (w.peer_msg) (void)hipIpcCloseMemHandle(w.peer_msg);
     if (w.peer_reply) (void)hipIpcCloseMemHandle(w.peer_reply);
     if (w.xslot) (void)hipFree(w.xslot);

@@ -6,8 +6,9 @@ C ABI (mpa_comm_set_task_lsq_batch + mpa_asyncmap), against the fp64 oracle
 Tolerance: normwise relative 1e-5, set from evidence.  Every kernel carries the residual
 as bf16 hi + lo (~2^-17 relative per element) and accumulates in fp32 over up to 2^20 rows;
 over every case of this file and every kernel the worst measured error is 2.42e-6
-(profiles/r02_c5_tolerance.txt: the default lsqp4, the eight-wave lsqp, the two passes,
-lsqf), so 1e-5 is about 4x the worst case and equals BASELINE's fp32 tolerance.
+(profiles/r02_c5_tolerance.txt: the default lsqp4 and the two passes; the measurement then
+also covered the single-pass variants since removed), so 1e-5 is about 4x the worst case and
+equals BASELINE's fp32 tolerance.
 """
 import numpy as np
 import pytest
@@ -195,27 +196,24 @@ def test_lsqb_descent_native_loop_matches_python_loop(M, monkeypatch, env):
 
 
 @pytest.mark.parametrize("env", [{}, {"MPA_LSQP": "c"}, {"MPA_LSQP": "8"}, {"MPA_LSQP": "0"}, {"MPA_LSQF": "1"},
-                                 {"MPA_LSQF": "1", "MPA_LSQF_DBG": "7"}, {"MPA_LSQQ": "1"}],
+                                 {"MPA_LSQF": "1", "MPA_LSQF_DBG": "7"}],
                          ids=["lsqp4_pairs_default", "lsqc_column_pairs", "lsqp_eight_waves", "two_pass",
-                              "lsqf_xcd_local_groups", "lsqf_cross_xcd_groups", "lsqq_quads"])
+                              "lsqf_xcd_local_groups", "lsqf_cross_xcd_groups"])
 @pytest.mark.parametrize("rows,cols,n", [(1, 32, 1), (4113, 544, 1), (3000, 2048, 3), (20000, 1024, 2),
                                          (2500, 1312, 2)])
 def test_single_pass_vs_oracle(M, monkeypatch, env, rows, cols, n):
-    """Every c5 kernel against the oracle: the default single pass by iterate halves
-    (lsqp4_kernel.hip: pairs of workgroups of one wave per SIMD, no exchange), column pairs
-    (lsqc_kernel.hip, MPA_LSQP=c: members split the columns and exchange per-block partial
-    products as tagged granules; one workgroup per row group at <= 1024 columns), the same
-    scheme cut into eight waves (lsqp_kernel.hip, MPA_LSQP=8), the two passes (MPA_LSQP=0), and
-    the opt-in single pass lsqf_kernel.hip (MPA_LSQF=1),
-    groups of P = ceil(cols / 512) workgroups exchanging partial residuals inside an XCD
-    (plain stores through the shared L2) or, with MPA_LSQF_DBG=7, every group treated as
-    spread over XCDs (write-through stores); and lsqq_kernel.hip (MPA_LSQQ=1), quads of
-    workgroups owning 16 iterates each.  Ragged rows and several tasks per launch;
-    repeated launches are bitwise identical (fixed summation orders)."""
+    """Both c5 kernels against the oracle: the default single pass by iterate halves
+    (lsqp4_kernel.hip: pairs of workgroups of one wave per SIMD, no exchange) and the two
+    passes (lsqb_kernel.hip, MPA_LSQP=0).  Ragged rows and several tasks per launch;
+    repeated launches are bitwise identical (fixed summation orders).
+
+    The other four parametrisations name single-pass variants that have left the tree
+    (DESIGN.md §10): nothing is left for them to run, so they skip, as they always did
+    against the product library."""
     import lsq
     import torch
-    if env not in ({}, {"MPA_LSQP": "0"}) and b"measurement build" not in M.lib().mpa_build_info():
-        pytest.skip("a c5 variant of the measurement build (make MEASURE=1, MPA_LIB=...): not in the product")
+    if env not in ({}, {"MPA_LSQP": "0"}):
+        pytest.skip("a c5 variant that is no longer in the tree: nothing is left to run")
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     A, B, X = _problem(n * rows, cols, seed=rows + cols + n)
@@ -225,7 +223,7 @@ def test_single_pass_vs_oracle(M, monkeypatch, env, rows, cols, n):
     assert list(rep) == [1] * n
     for i, (Ai, Bi) in enumerate(shards):
         err = lsq.rel_err(out[i], lsq.batched_shard_gradient(Ai, Bi, X, "bf16"))
-        print(f"lsqf rows={Ai.shape[0]} cols={cols} worker {i + 1} rel err {err:.3e}")
+        print(f"c5 rows={Ai.shape[0]} cols={cols} worker {i + 1} rel err {err:.3e}")
         assert err <= TOL, (i, err)
     again, _, _, _ = _run(M, torch, shards, cols, X, comm=comm, pool=pool, bufs=comm._bufs)
     assert np.array_equal(again.view(np.uint32), out.view(np.uint32))
