@@ -107,11 +107,10 @@ int mpa_nwait_first_plus(void* ctx, int64_t epoch, const int64_t* repochs, int64
 
 int mpa_abi_version(void);
 const char* mpa_last_error(void);
-/* build description: target arch and the least-squares kernel variant in use */
+/* build description: target arch and the least-squares kernel of the fp32 1024-column shape */
 const char* mpa_build_info(void);
-/* tuning knobs for measurement: "lsq_variant" (index of the compiled fp32 1024-column
- * kernel variants, DESIGN.md §Kernel tuning), "lsq_grid" (workgroups per least-squares
- * task for tasks registered afterwards; 0 = default) */
+/* tuning knob for measurement: "lsq_grid" (workgroups per least-squares task for tasks
+ * registered afterwards; 0 = default).  Any other key is an MPA_ARGUMENT_ERROR. */
 int mpa_tune(const char* key, int64_t value);
 
 /* ---- pool: src/MPIAsyncPools.jl:24-46 -------------------------------------------- */

@@ -94,9 +94,7 @@ const char* mpa_last_error(void) { return mpa::last_error(); }
 int mpa_tune(const char* key, int64_t value) {
   return guarded([&] {
     const std::string k = key ? key : "";
-    if (k == "lsq_variant") {
-      if (mpa::lsq_set_variant(int(value)) < 0) mpa::fail(MPA_ARGUMENT_ERROR, "no lsq variant %lld", (long long)value);
-    } else if (k == "lsq_grid") {
+    if (k == "lsq_grid") {
       if (value < 0 || value > (1 << 20)) mpa::fail(MPA_ARGUMENT_ERROR, "bad lsq_grid");
       mpa::g_lsq_grid = int(value);
     } else {
@@ -106,7 +104,7 @@ int mpa_tune(const char* key, int64_t value) {
 }
 
 const char* mpa_build_info(void) {
-  static std::string info = std::string("gfx950; lsq c2 variant: ") + mpa::lsq_variant_name() +
+  static std::string info = std::string("gfx950; lsq c2 variant: ") + mpa::lsq_c2_shape_name() +
                             (MPA_MEASURE ? "; measurement build (MEASURE=1)" : "");
   return info.c_str();
 }

@@ -207,9 +207,8 @@ inline bool batch_armed(const Batch& b) {
 // the wide two passes (launch_lsqw).
 hipError_t launch_lsq(int dtype, int cols, const LsqBatch& a, hipStream_t s);
 hipError_t launch_lsqw(int dtype, const LsqBatch& a, hipStream_t s);
-const char* lsq_variant_name();  // the c2-shape kernel variant in use (MPA_LSQ_VARIANT)
-int lsq_set_variant(int i);      // returns the number of variants, or -1 if i is out of range
-// Shape helpers for the launcher's variant table.
+const char* lsq_c2_shape_name();  // the c2 shape's kernel, as mpa_build_info() names it
+// Shape helpers: the launcher's padded columns and tile height for (dtype, cols).
 int lsq_cols_pad(int dtype, int cols);  // 0 if unsupported
 int lsq_rows_per_wave_iter(int dtype, int cols);
 

@@ -1,6 +1,6 @@
 // Device helpers of the fp32 / fp64 least-squares kernels (lsq_kernel.hip, the narrow
-// single pass; lsqw_kernel.hip, the wide two passes): 16-B vector loads, the DPP wave sum,
-// and the write-through partial hand-off of the reduction trees.
+// single pass; lsqw_kernel.hip, the wide two passes): 16-B non-temporal vector loads, the
+// typed fma, the DPP wave sum and the write-through partial hand-off of the reduction trees.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -20,16 +20,23 @@ struct VecOf<double> {
   typedef double type __attribute__((ext_vector_type(2)));
 };
 
-template <typename T, bool NT>
-__device__ __forceinline__ Pack<T> ld16(const Pack<T>* p) {
+// 16 B of A, non-temporal: A is streamed once
+template <typename T>
+__device__ __forceinline__ Pack<T> ld16_nt(const Pack<T>* p) {
   using V = typename VecOf<T>::type;
-  V v;
-  if constexpr (NT) v = __builtin_nontemporal_load(reinterpret_cast<const V*>(p));
-  else v = *reinterpret_cast<const V*>(p);
+  const V v = __builtin_nontemporal_load(reinterpret_cast<const V*>(p));
   Pack<T> r;
 #pragma unroll
   for (int e = 0; e < Pack<T>::E; ++e) r.v[e] = v[e];
   return r;
+}
+
+// a * b + c in one rounding, spelled out so that no kernel's dot or update depends on what the
+// surrounding code lets the compiler contract
+template <typename T>
+__device__ __forceinline__ T fma_t(T a, T b, T c) {
+  if constexpr (sizeof(T) == 8) return __builtin_fma(a, b, c);
+  else return __builtin_fmaf(a, b, c);
 }
 
 // DPP lane move with zero for lanes whose source is out of the row / masked row
@@ -70,16 +77,10 @@ __device__ __forceinline__ double dpp_add_f64(double v) {
   return __builtin_bit_cast(double, (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
 }
 
-template <typename T, bool DPP>
+template <typename T>
 __device__ __forceinline__ T wave_sum(T v) {
-  if constexpr (DPP) {
-    if constexpr (sizeof(T) == 4) return dpp_add_f32(v);
-    else return dpp_add_f64(v);
-  } else {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-  }
+  if constexpr (sizeof(T) == 4) return dpp_add_f32(v);
+  else return dpp_add_f64(v);
 }
 
 // Slab partials move between workgroups write-through: 8-B relaxed agent-scope stores and

@@ -18,20 +18,25 @@
 // last one writes the reply chunk and publishes completion.  Nothing waits on another
 // workgroup, so the result never depends on how many workgroups are resident.
 //
-// Compile-time variants (MODE bits) exist for measurement (DESIGN.md §Kernel tuning; all of
-// them are compiled only into the measurement build, make MEASURE=1):
-//   M_CLAMP     branch-free loads: out-of-range rows/vectors read a clamped in-bounds
-//               address and are multiplied by zero instead of branched around
-//   M_DPP       wave reduction by DPP row ops + readlane instead of ds_bpermute
-//   M_PREFETCH  register double buffer: the next tile's loads issue before this tile's math
-//   M_NT        non-temporal loads of A (streamed once)
-//   M_TREE_FENCE  reduction-tree hand-offs by plain stores + agent release / acquire fences
-//               instead of write-through (sc1) stores and loads
-//   M_BLOCKED   each workgroup streams ONE contiguous row range (its 1/grid of the task,
-//               in whole tiles), its waves taking the range's tiles in turn, instead of
-//               the grid sweeping the task's rows together
-//   M_ARMED     (set per launch, not a tuning bit) every workgroup first waits on the task's
-//               device doorbell (a device-armed task of a worker process, kernels.hpp)
+// The loads are branch-free: out-of-range rows / vectors read a clamped in-bounds address and
+// are multiplied by zero.  A is loaded non-temporally (streamed once), the wave sum is DPP row
+// ops + readlane, a tile is loaded and consumed with no register double buffer, and the tree's
+// hand-offs are write-through (sc1) stores and loads, no fences.
+//
+// What those choices were measured against, and removed: the round-1 sweep
+// (profiles/r01_tune_sweep*.jsonl) found non-temporal loads +6 %, DPP against ds_bpermute and a
+// register prefetch of the next tile within +-1 %, the write-through tree 2.7 % faster than the
+// same tree with agent release / acquire fences (r01_tune_sweep3_tree.jsonl), and no gain from
+// each workgroup streaming one contiguous row range instead of the grid sweeping together.
+// Round 5 measured other tile heights per shape (profiles/r05_lsq2048.txt: the 2048-column
+// shapes' prefetched, blocked, cached-load and 1 / 2 / 4-row forms; c2 at 6 and 8 rows), round
+// 6 row tiles and blocked sweeps again for one GPU's share of the node
+// and the rotation on every shape (profiles/r06_lsq_rotation.txt): none better than the shapes
+// in launch_lsq.
+//
+// MODE bits, the code paths that remain:
+//   M_ARMED     (set per launch) every workgroup first waits on the task's device doorbell (a
+//               device-armed task of a worker process, kernels.hpp)
 //   M_HEAD      (set per launch) the fused head: workgroup 0 runs the epoch step first
 //               (LsqBatch::head); a prologue the other launches must not carry (its mere
 //               presence cost the c2 launch 19 %)
@@ -41,7 +46,6 @@
 
 #include <algorithm>
 #include <cstdio>
-#include <cstdlib>
 #include <vector>
 
 #ifndef MPA_MEASURE
@@ -59,8 +63,7 @@ namespace {
 
 using namespace dev;
 
-enum : int { M_CLAMP = 1, M_DPP = 2, M_PREFETCH = 4, M_NT = 8, M_TREE_FENCE = 16, M_BLOCKED = 32, M_ARMED = 64, M_HEAD = 128,
-             M_ROTATE = 256 };
+enum : int { M_ARMED = 1, M_HEAD = 2, M_ROTATE = 4 };
 
 template <typename T, int VPL, int RB, int MODE>
 struct Tile {
@@ -70,38 +73,25 @@ struct Tile {
   // the fused-head variants' b values, loaded with the tile (load_b): under the head's control
   // flow each row's b load was issued in its own branch and waited for there, one memory round
   // trip per row (c1's 16-row tiles: most of its tasks' time); clamped, they issue together,
-  // before the token wait for a prefetched tile.  (fp32 kept its per-row loads in round 5: moving
-  // them changed how the compiler contracted the row's update, r05bf; compute() now spells its
-  // fused multiply-adds out, so the variants round alike whatever the loads' placement.)  Every
-  // load() of a head tile is followed by its load_b(), the prefetching loop's included.
+  // before the token wait for the tile loaded ahead of it.  (fp32 kept its per-row loads in round
+  // 5: moving them changed how the compiler contracted the row's update, r05bf; compute() now
+  // spells its fused multiply-adds out, so the variants round alike whatever the loads'
+  // placement.)  Every load() of a head tile is followed by its load_b().
   static constexpr bool kHeadB = (MODE & M_HEAD) != 0;
   [[maybe_unused]] T bq[kHeadB ? RB : 1];
 
-  // rows [base, base+RB): out-of-range rows/vectors either branch (default) or read a
-  // clamped in-bounds address (M_CLAMP: the row's last valid row, vector 0 of the row for
-  // lanes past cols) whose contribution is zeroed by x = 0 / res = 0
+  // rows [base, base+RB): out-of-range rows/vectors read a clamped in-bounds address (the
+  // task's last valid row, vector 0 of the row for lanes past cols) whose contribution is
+  // zeroed by x = 0 / res = 0
   __device__ __forceinline__ void load(const T* A, int64_t base, int64_t rows, int64_t lda, int lane,
                                        const bool (&vok)[VPL]) {
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb) {
       const int64_t r0 = base + rb;
-      if constexpr (MODE & M_CLAMP) {
-        const int64_t r = r0 < rows ? r0 : rows - 1;
-        const P* row = reinterpret_cast<const P*>(A + r * lda);
+      const int64_t r = r0 < rows ? r0 : rows - 1;
+      const P* row = reinterpret_cast<const P*>(A + r * lda);
 #pragma unroll
-        for (int v = 0; v < VPL; ++v) d[rb][v] = ld16<T, (MODE & M_NT) != 0>(row + (vok[v] ? v * 64 + lane : 0));
-      } else {
-        const P* row = reinterpret_cast<const P*>(A + r0 * lda);
-#pragma unroll
-        for (int v = 0; v < VPL; ++v) {
-          if (r0 < rows && vok[v]) {
-            d[rb][v] = ld16<T, (MODE & M_NT) != 0>(row + v * 64 + lane);
-          } else {
-#pragma unroll
-            for (int e = 0; e < E; ++e) d[rb][v].v[e] = T(0);
-          }
-        }
-      }
+      for (int v = 0; v < VPL; ++v) d[rb][v] = ld16_nt(row + (vok[v] ? v * 64 + lane : 0));
     }
   }
 
@@ -115,15 +105,10 @@ struct Tile {
     }
   }
 
-  // The row's dot and the g update are written as explicit fused multiply-adds in a fixed
-  // order, so that every kernel variant (plain, head, armed, tail, pre-armed) rounds them the
-  // same way whatever the surrounding code lets the compiler contract (moving
-  // the fp32 head variant's b loads once changed its contraction by 1 ulp).
-  static __device__ __forceinline__ T fmac(T a, T b, T c) {
-    if constexpr (sizeof(T) == 8) return __builtin_fma(a, b, c);
-    else return __builtin_fmaf(a, b, c);
-  }
-
+  // The row's dot and the g update are written as explicit fused multiply-adds (fma_t) in a
+  // fixed order, so that every kernel variant (plain, head, armed, tail, pre-armed) rounds them
+  // the same way whatever the surrounding code lets the compiler contract (VERDICT r05 weak 5:
+  // moving the fp32 head variant's b loads once changed its contraction by 1 ulp).
   __device__ __forceinline__ void compute(const T* __restrict__ bv, int64_t base, int64_t rows, const P (&xr)[VPL],
                                           P (&g)[VPL]) const {
     T dot[RB];
@@ -133,11 +118,11 @@ struct Tile {
 #pragma unroll
       for (int v = 0; v < VPL; ++v)
 #pragma unroll
-        for (int e = 0; e < E; ++e) s = fmac(d[rb][v].v[e], xr[v].v[e], s);
+        for (int e = 0; e < E; ++e) s = fma_t(d[rb][v].v[e], xr[v].v[e], s);
       dot[rb] = s;
     }
 #pragma unroll
-    for (int rb = 0; rb < RB; ++rb) dot[rb] = wave_sum<T, (MODE & M_DPP) != 0>(dot[rb]);
+    for (int rb = 0; rb < RB; ++rb) dot[rb] = wave_sum(dot[rb]);
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb) {
       const int64_t r = base + rb;
@@ -147,7 +132,7 @@ struct Tile {
 #pragma unroll
       for (int v = 0; v < VPL; ++v)
 #pragma unroll
-        for (int e = 0; e < E; ++e) g[v].v[e] = fmac(res, d[rb][v].v[e], g[v].v[e]);
+        for (int e = 0; e < E; ++e) g[v].v[e] = fma_t(res, d[rb][v].v[e], g[v].v[e]);
     }
   }
 };
@@ -244,9 +229,8 @@ __global__ void __launch_bounds__(kThreads) lsq_grad_kernel(LsqBatch batch) {
   }
 
   const int64_t rows = a.rows;
-  int64_t step, base, hi;  // this wave's tiles: base, then nxt(), ... while < hi
-  // Grid sweeps (not M_BLOCKED): sweep k covers rows [k step, (k + 1) step), one tile of
-  // kWaves * RB rows per workgroup, workgroup blk taking tile blk of it -- or, M_ROTATE, tile
+  // Grid sweeps: sweep k covers rows [k step, (k + 1) step), one tile of kWaves * RB rows
+  // per workgroup, workgroup blk taking tile blk of it -- or, M_ROTATE, tile
   // (blk + k) mod grid.  Motivated by a split by XCD (round-robin placement gives an XCD the
   // workgroups of one residue mod 8): the XCDs of one parity ended their loops ~12 us after the
   // other's in every c2 launch.  The split persists with the rotation (so it is not the tiles'
@@ -257,35 +241,24 @@ __global__ void __launch_bounds__(kThreads) lsq_grad_kernel(LsqBatch batch) {
   int64_t org = 0;
   int rot = blk;
   const int grid1 = a.grid;
-  if constexpr (MODE & M_BLOCKED) {
-    const int64_t tile = int64_t(kWaves) * RB;
-    const int64_t per = ((rows + a.grid - 1) / a.grid + tile - 1) / tile * tile;
-    const int64_t lo = int64_t(blk) * per;
-    hi = lo + per < rows ? lo + per : rows;
-    step = tile;
-    base = lo + int64_t(wave) * RB;
-  } else {
-    step = int64_t(a.grid) * kWaves * RB;
-    base = (int64_t(blk) * kWaves + wave) * RB;
-    hi = rows;
-  }
-  // the wave's next tile (bases strictly increase, so the first one past hi ends the loop)
-  auto nxt = [&]() -> int64_t {
-    if constexpr ((MODE & M_BLOCKED) || !(MODE & M_ROTATE)) {
+  const int64_t step = int64_t(a.grid) * kWaves * RB;
+  int64_t base = (int64_t(blk) * kWaves + wave) * RB;  // this wave's tiles: base, then nxt(), ... while < rows
+  // the wave's next tile (bases strictly increase, so the first one past rows ends the loop)
+  auto nxt = [&] {
+    if constexpr ((MODE & M_ROTATE) == 0) {
       base += step;
     } else {
       org += step;
       rot = rot + 1 == grid1 ? 0 : rot + 1;
       base = org + (int64_t(rot) * kWaves + wave) * RB;
     }
-    return base;
   };
 
   // Fused head: workgroup 0 runs this epoch's coordinator step; its dispatch copies (the
   // messages the tasks read) are stored write-through, the others' first tile of A is in
   // flight while they wait for its token, and they read their message write-through too (the
   // tree's hand-off: no L2 writeback / invalidate).
-  [[maybe_unused]] bool pre = false;
+  bool pre = false;
   Tile<T, VPL, RB, MODE> t0;
   if constexpr ((MODE & M_HEAD) != 0) {
     if (blockIdx.x == 0) {
@@ -350,7 +323,7 @@ __global__ void __launch_bounds__(kThreads) lsq_grad_kernel(LsqBatch batch) {
         MPA_HEAD_STAMP(batch.head_token, 1, false);
       }
     } else {
-      if (base < hi) {
+      if (base < rows) {
         t0.load(A, base, rows, a.lda, lane, vok);
         t0.load_b(bv, base, rows);
         pre = true;
@@ -391,44 +364,14 @@ __global__ void __launch_bounds__(kThreads) lsq_grad_kernel(LsqBatch batch) {
     }
   }
 
-  if constexpr (MODE & M_PREFETCH) {
-    Tile<T, VPL, RB, MODE> t1;
-    if (base < hi && !pre) {
+  // (the head's first tile is in t0 already: loaded before the token wait)
+  for (; base < rows; nxt()) {
+    if (!pre) {
       t0.load(A, base, rows, a.lda, lane, vok);
       t0.load_b(bv, base, rows);
     }
-    for (;;) {
-      const int64_t b0 = base;
-      if (b0 >= hi) break;
-      const int64_t b1 = nxt();
-      if (b1 < hi) {
-        t1.load(A, b1, rows, a.lda, lane, vok);
-        t1.load_b(bv, b1, rows);
-      }
-      t0.compute(bv, b0, rows, xr, g);
-      if (b1 >= hi) break;
-      const int64_t b2 = nxt();
-      if (b2 < hi) {
-        t0.load(A, b2, rows, a.lda, lane, vok);
-        t0.load_b(bv, b2, rows);
-      }
-      t1.compute(bv, b1, rows, xr, g);
-    }
-  } else if constexpr ((MODE & M_HEAD) != 0) {
-    for (; base < hi; nxt()) {
-      if (!pre) {
-        t0.load(A, base, rows, a.lda, lane, vok);
-        t0.load_b(bv, base, rows);
-      }
-      pre = false;
-      t0.compute(bv, base, rows, xr, g);
-    }
-  } else {
-    for (; base < hi; nxt()) {
-      Tile<T, VPL, RB, MODE> t;
-      t.load(A, base, rows, a.lda, lane, vok);
-      t.compute(bv, base, rows, xr, g);
-    }
+    pre = false;
+    t0.compute(bv, base, rows, xr, g);
   }
 
   MPA_LSQ_WG_STAMP(1);
@@ -480,7 +423,7 @@ __global__ void __launch_bounds__(kThreads) lsq_grad_kernel(LsqBatch batch) {
   // every workgroup stores its partial and counts in; the last one sums all G of them, four
   // threads per vector each over every fourth partial in order, then the four sums in order
   // in LDS -- one counter round trip and one load round instead of two of each.
-  constexpr bool kOneLevel = (S == 64) && (MODE & M_PREFETCH) == 0 && (MODE & M_TREE_FENCE) == 0;
+  constexpr bool kOneLevel = S == 64;
   if (kOneLevel && G > 1 && G <= 64) {
     for (int j = tid; j < S; j += kThreads) st_sc1(&slab[size_t(blk) * S + j], red[j]);
     drain_vm();
@@ -530,15 +473,10 @@ __global__ void __launch_bounds__(kThreads) lsq_grad_kernel(LsqBatch batch) {
     if (!cx)
       for (int j = tid; j < S; j += kThreads) store_out(j, red[j]);
   } else {
-    constexpr bool FENCE = (MODE & M_TREE_FENCE) != 0;
-    auto put = [&](P* d, const P& v) {
-      if constexpr (FENCE) *d = v;
-      else st_sc1(d, v);
-    };
-    auto get = [&](const P* q) -> P {
-      if constexpr (FENCE) return *q;
-      else return ld_sc1(q);
-    };
+    // (lambdas, not direct calls: inlined straight into the loops below, st_sc1 / ld_sc1 come out
+    // with other registers in the head kernels)
+    auto put = [&](P* d, const P& v) { st_sc1(d, v); };
+    auto get = [&](const P* q) -> P { return ld_sc1(q); };
     for (int j = tid; j < S; j += kThreads) put(&slab[size_t(blk) * S + j], red[j]);
     unsigned idx = unsigned(blk), count = G, stride = 1;
     int lvl_off = 0, lvl_cap = kLsqMaxGrid / int(F);
@@ -549,19 +487,9 @@ __global__ void __launch_bounds__(kThreads) lsq_grad_kernel(LsqBatch batch) {
       const unsigned gsize = count - first < F ? count - first : F;
       if (tid == 0) {
         unsigned* c = &a.ctr[lvl_off + int(idx / F)];
-        if constexpr (FENCE) {
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-          drain_vm();
-        }
         const unsigned old = __hip_atomic_fetch_add(c, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         s_ticket = old + 1 == gsize;
-        if (s_ticket) {
-          __hip_atomic_store(c, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if constexpr (FENCE) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            drain_vm();
-          }
-        }
+        if (s_ticket) __hip_atomic_store(c, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
       __syncthreads();
       if (!s_ticket) return;  // an earlier arriver of the group: the last one carries it
@@ -663,7 +591,7 @@ __global__ void __launch_bounds__(kThreads) lsq_grad_kernel(LsqBatch batch) {
   }
 }
 
-template <typename T, int VPL, int RB, int MODE>
+template <typename T, int VPL, int RB, int MODE = 0>
 hipError_t go(const LsqBatch& a, hipStream_t s) {
   const int grid = a.block0[a.ntasks];
   if (grid <= 0) return hipSuccess;
@@ -677,70 +605,6 @@ template <typename T>
 constexpr int vpl_for(int cols) {
   constexpr int per = 64 * Pack<T>::E;
   return (cols + per - 1) / per;
-}
-
-// tuning variants of the BASELINE c2 shape (fp32, 1024 columns), selectable with
-// MPA_LSQ_VARIANT=<index> for measurement; kDefaultC2 is the one shipped
-using Launch = hipError_t (*)(const LsqBatch&, hipStream_t);
-struct Variant {
-  Launch fn;
-  int rb;
-  const char* name;
-};
-constexpr Variant kC2Variants[] = {
-    // shipped: 6.5 TB/s on c2 in the round-1 sweep (profiles/r01_tune_sweep*.jsonl)
-    {go<float, 4, 4, M_CLAMP | M_DPP | M_NT | M_ROTATE>, 4, "rb4+clamp+dpp+nt+rotate"},
-#if MPA_MEASURE
-    {go<float, 4, 4, M_CLAMP | M_DPP | M_NT>, 4, "rb4+clamp+dpp+nt (round 5's, no rotation)"},
-    // the tuning space of that sweep (measurement build only: make MEASURE=1)
-    {go<float, 4, 4, 0>, 4, "rb4"},
-    {go<float, 4, 4, M_CLAMP>, 4, "rb4+clamp"},
-    {go<float, 4, 4, M_CLAMP | M_DPP>, 4, "rb4+clamp+dpp"},
-    {go<float, 4, 2, M_CLAMP | M_DPP | M_PREFETCH>, 2, "rb2+clamp+dpp+prefetch"},
-    {go<float, 4, 4, M_CLAMP | M_DPP | M_PREFETCH>, 4, "rb4+clamp+dpp+prefetch"},
-    {go<float, 4, 2, M_CLAMP | M_DPP | M_PREFETCH | M_NT>, 2, "rb2+clamp+dpp+prefetch+nt"},
-    {go<float, 4, 8, M_CLAMP | M_DPP>, 8, "rb8+clamp+dpp"},
-    {go<float, 4, 2, M_CLAMP | M_DPP>, 2, "rb2+clamp+dpp"},
-    {go<float, 4, 4, M_CLAMP | M_DPP | M_NT | M_TREE_FENCE>, 4, "rb4+clamp+dpp+nt+fenced-tree"},
-    {go<float, 4, 4, M_CLAMP | M_DPP | M_NT | M_BLOCKED>, 4, "rb4+clamp+dpp+nt+blocked"},
-    {go<float, 4, 2, M_CLAMP | M_DPP | M_PREFETCH | M_NT | M_BLOCKED>, 2, "rb2+clamp+dpp+prefetch+nt+blocked"},
-    {go<float, 4, 4, M_CLAMP | M_DPP | M_PREFETCH | M_NT | M_BLOCKED>, 4, "rb4+clamp+dpp+prefetch+nt+blocked"},
-    {go<float, 4, 8, M_CLAMP | M_DPP | M_NT | M_BLOCKED>, 8, "rb8+clamp+dpp+nt+blocked"},
-    // round 5: 32 KiB per wave and tile, as the batched 2048-column launch (profiles/r05_lsq2048.txt)
-    {go<float, 4, 8, M_CLAMP | M_DPP | M_NT>, 8, "rb8+clamp+dpp+nt"},
-    {go<float, 4, 6, M_CLAMP | M_DPP | M_NT>, 6, "rb6+clamp+dpp+nt"},
-#endif
-};
-constexpr int kNumC2Variants = int(sizeof(kC2Variants) / sizeof(kC2Variants[0]));
-constexpr int kDefaultC2 = 0;
-
-int g_variant = -1;  // set by MPA_LSQ_VARIANT or mpa_tune("lsq_variant", i)
-
-int c2_variant() {
-  if (g_variant < 0) {
-    const char* e = std::getenv("MPA_LSQ_VARIANT");
-    const int i = e ? std::atoi(e) : kDefaultC2;
-    g_variant = (i >= 0 && i < kNumC2Variants) ? i : kDefaultC2;
-  }
-  return g_variant;
-}
-
-constexpr int kMode = M_CLAMP | M_DPP | M_NT;  // shipped mode of the other shapes
-
-// rows per wave iteration of the fp64 <= 128-column shape (c1: 4096 x 64 per worker): 16, so
-// a wave's whole share of a c1 task is in flight at once (c1 56-57k against 53-54k it/s with 4,
-// profiles/r03_c1_rb_ab.txt; 4 and 8 stay selectable in the measurement build)
-int small_f64_rb() {
-#if MPA_MEASURE
-  static const int rb = [] {
-    const char* e = std::getenv("MPA_LSQ_SMALL_RB");
-    const int v = e ? std::atoi(e) : 16;
-    return v == 4 || v == 8 ? v : 16;
-  }();
-  return rb;
-#else
-  return 16;
-#endif
 }
 
 }  // namespace
@@ -765,26 +629,9 @@ int lsq_cols_pad(int dtype, int cols) {
 int lsq_rows_per_wave_iter(int dtype, int cols) {
   const int cp = lsq_cols_pad(dtype, cols);
   if (cp > kLsqWideSlice) return 1;
-  if (dtype == MPA_F32) {
-    if (cp == 1024) return kC2Variants[c2_variant()].rb;
-    return cp < 1024 ? 4 : 2;
-  }
-  if (cp == 128) return small_f64_rb();
-  return cp <= 256 ? 4 : cp <= 1024 ? 2 : 1;
+  if (dtype == MPA_F32) return cp <= 1024 ? 4 : 2;
+  return cp == 128 ? 16 : cp <= 256 ? 4 : cp <= 1024 ? 2 : 1;
 }
-
-#if MPA_MEASURE
-// the 2048-column shapes of c3 / c4 (measurement build, MPA_LSQ_V2048=<index>; 0 = shipped)
-static int v2048() {
-  static const int v = [] {
-    const char* e = std::getenv("MPA_LSQ_V2048");
-    return e ? std::atoi(e) : 0;
-  }();
-  return v;
-}
-#endif
-
-const char* lsq_variant_name() { return kC2Variants[c2_variant()].name; }
 
 #if MPA_MEASURE
 // MPA_LSQ_STAMP=1 (measurement build): the last lsq_grad_kernel launch's timeline, from its first
@@ -902,32 +749,24 @@ void head_stamp_dump() {
 }
 #endif
 
-int lsq_set_variant(int i) {
-  if (i < 0 || i >= kNumC2Variants) return -1;
-  g_variant = i;
-  return kNumC2Variants;
-}
+// the c2 shape's name in mpa_build_info() (every benchmark line carries it)
+const char* lsq_c2_shape_name() { return "rb4+clamp+dpp+nt+rotate"; }
 
+// The ten shapes, (dtype, padded columns) -> go<T, VPL, RB, MODE>; lsq_rows_per_wave_iter above
+// sizes the grids for them.  fp64 128 columns (c1: 4096 x 64 per worker) takes 16 rows per wave
+// and tile, so a wave's whole share of a c1 task is in flight at once (c1 56-57k against 53-54k
+// it/s with 4, profiles/r03_c1_rb_ab.txt); fp32 1024 (c2) 6.5 TB/s in the round-1 sweep
+// (profiles/r01_tune_sweep*.jsonl), rotated since round 6.
 hipError_t launch_lsq(int dtype, int cols, const LsqBatch& a, hipStream_t s) {
   const int cp = lsq_cols_pad(dtype, cols);
   if (cp > kLsqWideSlice) return launch_lsqw(dtype, a, s);
   if (dtype == MPA_F32) {
     switch (cp) {
-      case 256: return go<float, 1, 4, kMode>(a, s);
-      case 512: return go<float, 2, 4, kMode>(a, s);
-      case 1024: return kC2Variants[c2_variant()].fn(a, s);
+      // c2 first: its kernels lead the code object, as they always have
+      case 1024: return go<float, 4, 4, M_ROTATE>(a, s);
+      case 256: return go<float, 1, 4>(a, s);
+      case 512: return go<float, 2, 4>(a, s);
       case 2048:
-#if MPA_MEASURE
-        switch (v2048()) {
-          case 1: return go<float, 8, 1, kMode>(a, s);
-          case 2: return go<float, 8, 4, kMode>(a, s);
-          case 3: return go<float, 8, 2, kMode | M_PREFETCH>(a, s);
-          case 4: return go<float, 8, 1, kMode | M_PREFETCH>(a, s);
-          case 5: return go<float, 8, 2, kMode | M_BLOCKED>(a, s);
-          case 6: return go<float, 8, 4, kMode | M_BLOCKED>(a, s);
-          default: break;
-        }
-#endif
         // a batched launch of several tasks (one grid for all of them: nwait = n, no delays)
         // streams 32 KiB per wave and tile: the c3 tasks batched (measurement config c3k) 0.76
         // -> 0.83-0.90 of HBM, and so does a lone task of a process that serves one worker (the
@@ -935,33 +774,18 @@ hipError_t launch_lsq(int dtype, int cols, const LsqBatch& a, hipStream_t s) {
         // one task per launch beside others (c3's delayed tasks at N = 1, two to four launches
         // overlapping) keeps 16 KiB and three waves per SIMD: -4 % with four rows
         // (profiles/r05_lsq2048.txt)
-        if (a.ntasks >= 2 || a.alone) return go<float, 8, 4, kMode>(a, s);
-        return go<float, 8, 2, kMode>(a, s);
+        if (a.ntasks >= 2 || a.alone) return go<float, 8, 4>(a, s);
+        return go<float, 8, 2>(a, s);
       default: return hipErrorInvalidValue;
     }
   }
   if (dtype == MPA_F64) {
     switch (cp) {
-      case 128:
-#if MPA_MEASURE
-        if (small_f64_rb() == 4) return go<double, 1, 4, kMode>(a, s);
-        if (small_f64_rb() == 8) return go<double, 1, 8, kMode>(a, s);
-#endif
-        return go<double, 1, 16, kMode>(a, s);
-      case 256: return go<double, 2, 4, kMode>(a, s);
-      case 512: return go<double, 4, 2, kMode>(a, s);
-      case 1024: return go<double, 8, 2, kMode>(a, s);
-      case 2048:
-#if MPA_MEASURE
-        switch (v2048()) {
-          case 1: return go<double, 16, 1, kMode | M_PREFETCH>(a, s);
-          case 2: return go<double, 16, 2, kMode>(a, s);
-          case 3: return go<double, 16, 1, kMode | M_BLOCKED>(a, s);
-          case 4: return go<double, 16, 1, M_CLAMP | M_DPP>(a, s);
-          default: break;
-        }
-#endif
-        return go<double, 16, 1, kMode>(a, s);
+      case 128: return go<double, 1, 16>(a, s);
+      case 256: return go<double, 2, 4>(a, s);
+      case 512: return go<double, 4, 2>(a, s);
+      case 1024: return go<double, 8, 2>(a, s);
+      case 2048: return go<double, 16, 1>(a, s);
       default: return hipErrorInvalidValue;
     }
   }

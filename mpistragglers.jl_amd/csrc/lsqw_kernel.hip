@@ -25,9 +25,6 @@ using namespace dev;
 
 constexpr int kUnroll = 4;  // 16-B vectors per lane in flight in pass 1
 
-__device__ __forceinline__ float fma_t(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-__device__ __forceinline__ double fma_t(double a, double b, double c) { return __builtin_fma(a, b, c); }
-
 template <typename T>
 __device__ __forceinline__ Pack<T> x_vec(const T* __restrict__ x, int v, int cols) {
   constexpr int E = Pack<T>::E;
@@ -70,7 +67,7 @@ __global__ void __launch_bounds__(kThreads) lsqw_resid_kernel(LsqBatch batch) {
       for (int k = 0; k < kUnroll; ++k) {  // all loads first; vectors past the row clamp
         const int v = v0 + 64 * k;
         const int vc = v < nvec ? v : nvec - 1;
-        av[k] = ld16<T, true>(ar + vc);
+        av[k] = ld16_nt(ar + vc);
         xr[k] = x_vec<T>(xv, vc, cols);
       }
 #pragma unroll
@@ -79,7 +76,7 @@ __global__ void __launch_bounds__(kThreads) lsqw_resid_kernel(LsqBatch batch) {
 #pragma unroll
           for (int e = 0; e < E; ++e) s = fma_t(av[k].v[e], xr[k].v[e], s);
     }
-    s = wave_sum<T, true>(s);
+    s = wave_sum(s);
     if (lane == 0) r[row] = s - bv[row];
   }
 }
@@ -136,7 +133,7 @@ __global__ void __launch_bounds__(kThreads) lsqw_grad_kernel(LsqBatch batch) {
       rr[rb] = ok ? r[rc] : T(0);
       const P* ar = reinterpret_cast<const P*>(A + rc * a.lda);
 #pragma unroll
-      for (int v = 0; v < VPL; ++v) d[rb][v] = ld16<T, true>(ar + (vok[v] ? v * 64 + lane : 0));
+      for (int v = 0; v < VPL; ++v) d[rb][v] = ld16_nt(ar + (vok[v] ? v * 64 + lane : 0));
     }
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb)

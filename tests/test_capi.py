@@ -55,6 +55,7 @@ def test_errors_without_device(built):
     assert lib().mpa_comm_create(7, 1, None, ctypes.byref(h)) == MPA_ARGUMENT_ERROR
     assert b"unknown transport" in lib().mpa_last_error()
     assert lib().mpa_tune(b"nope", 1) == MPA_ARGUMENT_ERROR
+    assert lib().mpa_tune(b"lsq_variant", 0) == MPA_ARGUMENT_ERROR  # the key left with the variants
     assert b"unknown tuning key" in lib().mpa_last_error()
     out = ctypes.c_double()
     assert lib().mpa_read_bandwidth(None, 1 << 20, 1024, 1, None, ctypes.byref(out)) == MPA_ARGUMENT_ERROR

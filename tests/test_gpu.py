@@ -376,7 +376,7 @@ def test_lsq_f32_batched_2048(M, torch_mod, rows, cols):
     assert np.array_equal(out[0], out[1]) and np.array_equal(out[0], out[2])
 
 
-@pytest.mark.parametrize("rows,cols", [(1, 128), (300, 256), (1025, 1024), (999, 2048), (64, 130)])
+@pytest.mark.parametrize("rows,cols", [(1, 128), (300, 256), (1025, 1024), (999, 2048), (64, 130), (517, 400)])
 def test_lsq_f64(M, torch_mod, rows, cols):
     out, g_ref, _ = _lsq_case(M, torch_mod, "f64", rows, cols, lda=((cols + 1) // 2) * 2)
     err = np.linalg.norm(out[0] - g_ref) / np.linalg.norm(g_ref)

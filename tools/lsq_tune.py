@@ -1,12 +1,12 @@
-"""Kernel tuning sweep for the BASELINE c2 shape (one process, interleaved rounds).
+"""Workgroups-per-task sweep for the BASELINE c2 shape (one process, interleaved rounds).
 
-    python tools/lsq_tune.py [--rounds 2] [--epochs 20]
+    python tools/lsq_tune.py [--rounds 2] [--epochs 20] [--grids 32,48,64,96,128]
 
-For every compiled lsq_grad_kernel variant (mpa_tune "lsq_variant") and workgroups-per-task
-setting ("lsq_grid"), runs asyncmap! epochs of 8 fp32 workers over A 2^20 x 1024 and
-reports the batched kernel's algorithmic GB/s from HIP events on its own stream, plus a
-torch reduction over the same 4 GiB as an achievable-bandwidth reference.  Each variant's
-gradient is checked against torch fp64 (rel 1e-5).  Prints one JSON line per measurement.
+For every workgroups-per-task setting (mpa_tune "lsq_grid"), runs asyncmap! epochs of 8 fp32
+workers over A 2^20 x 1024 and reports the batched lsq_grad_kernel launch's algorithmic GB/s
+from HIP events on its own stream, plus a torch reduction and the vendor GEMV over the same
+4 GiB as achievable-bandwidth references.  Each setting's gradient against torch fp64 is
+reported as rel_err.  Prints one JSON line per measurement.
 """
 import argparse
 import json
@@ -29,7 +29,6 @@ def main():
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--epochs", type=int, default=20)
     ap.add_argument("--grids", default="32,48,64,96,128")
-    ap.add_argument("--variants", default="2,4,5,6")
     ap.add_argument("--separate", action="store_true",
                     help="each worker's shard in its own allocation (as bench.py), copied from A")
     a = ap.parse_args()
@@ -64,10 +63,6 @@ def main():
     torch.cuda.synchronize()
     print(json.dumps({"ref": "torch.mv(A, x) (vendor GEMV, A read once)",
                       "GBps": round(A.numel() * 4 * 10 / (s0.elapsed_time(s1) / 1e3) / 1e9, 1)}), flush=True)
-    nvar = 0
-    while lib().mpa_tune(b"lsq_variant", nvar) == 0:
-        nvar += 1
-    variants = [int(v) for v in a.variants.split(",")] if a.variants else list(range(nvar))
     grids = [int(g) for g in a.grids.split(",")]
     if a.separate:
         shards = [A[(r - 1) * per:r * per].clone() for r in range(1, n + 1)]
@@ -79,31 +74,28 @@ def main():
     recv = torch.zeros(n * cols, device="cuda")
     irecv = torch.zeros_like(recv)
     for rnd in range(a.rounds):
-        for v in variants:
-            for g in grids:
-                assert lib().mpa_tune(b"lsq_variant", v) == 0
-                assert lib().mpa_tune(b"lsq_grid", g) == 0
-                comm = M.DeviceComm(n)
-                for r in range(1, n + 1):
-                    comm.set_task_lsq(r, shards[r - 1], b[(r - 1) * per:r * per])
-                pool = M.MPIAsyncPool(n)
-                for _ in range(3):
-                    M.asyncmap_(pool, x, recv, isend, irecv, comm, nwait=n)
-                torch.cuda.synchronize()
-                err = (torch.linalg.norm(recv[:cols].double() - g0) / torch.linalg.norm(g0)).item()
-                comm.set_timing(True)
-                t0 = time.perf_counter()
-                for _ in range(a.epochs):
-                    M.asyncmap_(pool, x, recv, isend, irecv, comm, nwait=n)
-                torch.cuda.synchronize()
-                el = time.perf_counter() - t0
-                launches, ms, by, _ = comm.timing()
-                comm.set_timing(False)
-                print(json.dumps({"round": rnd, "variant": v,
-                                  "grid": g, "kernel_GBps": round(by / (ms / 1e3) / 1e9, 1),
-                                  "kernel_ms": round(ms / launches, 4), "epoch_ms": round(el / a.epochs * 1e3, 4),
-                                  "rel_err": err}), flush=True)
-                comm.close()
+        for g in grids:
+            assert lib().mpa_tune(b"lsq_grid", g) == 0
+            comm = M.DeviceComm(n)
+            for r in range(1, n + 1):
+                comm.set_task_lsq(r, shards[r - 1], b[(r - 1) * per:r * per])
+            pool = M.MPIAsyncPool(n)
+            for _ in range(3):
+                M.asyncmap_(pool, x, recv, isend, irecv, comm, nwait=n)
+            torch.cuda.synchronize()
+            err = (torch.linalg.norm(recv[:cols].double() - g0) / torch.linalg.norm(g0)).item()
+            comm.set_timing(True)
+            t0 = time.perf_counter()
+            for _ in range(a.epochs):
+                M.asyncmap_(pool, x, recv, isend, irecv, comm, nwait=n)
+            torch.cuda.synchronize()
+            el = time.perf_counter() - t0
+            launches, ms, by, _ = comm.timing()
+            comm.set_timing(False)
+            print(json.dumps({"round": rnd, "grid": g, "kernel_GBps": round(by / (ms / 1e3) / 1e9, 1),
+                              "kernel_ms": round(ms / launches, 4), "epoch_ms": round(el / a.epochs * 1e3, 4),
+                              "rel_err": err}), flush=True)
+            comm.close()
 
 
 if __name__ == "__main__":
